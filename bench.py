@@ -8,8 +8,12 @@ dropout 0.5 = the reference's default, main_itp_ddp_tar_super_node.py:466, submi
 N GPUs = one process per GPU (torch.distributed.run), weak scaling, RCCL all-reduce of
 the live gradients streamed out of the backward (savqa_amd.ddp).
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (fp32 MFMA
-GEMM, HIP-event timed) and the CPU oracle's throughput on the host as cpu_baseline.
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0).
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.
+--full adds what takes runs of its own: the roofline of the dominant kernel (fp32 MFMA
+GEMM, HIP-event timed, two probe steps), the per-kernel HBM report, the CPU oracle's
+throughput on the host as cpu_baseline, and with N > 1 the collectives' timing over
+--comm-steps diagnostic steps.
 """
 from __future__ import annotations
 
@@ -259,6 +263,43 @@ def committed_traffic(variant, workload="cfg2"):
         return None
 
 
+DUMP_ROWS = 4096  # --dump-outputs: sampled elements per parameter tensor
+
+
+def dump_outputs(path, model, loss, outs):
+    """Write what the last timed step computed as path/<name>.npy (float32): the step's
+    return values (the three heads' logits, the MIL-NCE terms, the loss) in full, and of its
+    side effect on the model, the gradients and the Adam-updated parameters, a fixed seeded
+    sample of up to DUMP_ROWS elements per live tensor in arena order (the whole arena is
+    ~1.8 GB at cfg 2). ~10 MB in all at cfg 2.
+
+    Inputs, weights and dropout seeds are the same from run to run, and every sum of the step
+    has a fixed order, so two runs of one build write the same arrays."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for name, t in zip(("logits_concat", "logits_vis", "logits_syb", "mil_nce_obj",
+                        "mil_nce_rel"), outs):
+        if torch.is_tensor(t):  # the relation term is a plain 0 in objects-only mode
+            arrays[name] = t.detach()
+    arena = model._arena
+    gen = torch.Generator().manual_seed(20240)
+    idx = []
+    for n in arena.live_names:
+        o, shp = arena.offsets[n]
+        numel = int(torch.Size(shp).numel())
+        k = min(numel, DUMP_ROWS)
+        idx.append(o + (torch.arange(numel) if k == numel
+                        else torch.randint(0, numel, (k,), generator=gen).sort().values))
+    idx = torch.cat(idx).to(arena.flat.device)
+    arrays["params_sample"] = arena.flat[idx]
+    if arena.grad is not None:
+        arrays["grads_sample"] = arena.grad[idx]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(t.float().cpu().numpy().astype(np.float32)))
+
+
 def _self_launch(n):
     """Run this command as `python -m torch.distributed.run --nproc-per-node n` (rendezvous on
     127.0.0.1, a free port) in a child process and return its exit status. Called before any
@@ -302,9 +343,17 @@ def main():
                          "features + bf16, 1024/GPU); rel = the super-node relation branch")
     ap.add_argument("--dropout", type=float, default=0.5,
                     help="dropout_rate (reference training default 0.5, main:466)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (logits, "
+                         "MIL-NCE terms, loss, a seeded sample of the gradients and the updated "
+                         "parameters) as DIR/<name>.npy, float32 (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline probe steps, the CPU "
+                         "oracle baseline (cfg2, 1 GPU) and, N > 1, the --comm-steps diagnostic "
+                         "steps; a plain run reports null for them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the probe steps")
     ap.add_argument("--serial", action="store_true",
                     help="run both stacks on one stream (per-kernel profiling)")
     ap.add_argument("--bucket-mb", type=float, default=64.0,
@@ -313,9 +362,11 @@ def main():
                     help="N > 1: backward schedule (engine.vis_gate): auto (= enc4 with an "
                          "all-reduce), concurrent, enc1..enc6, dec, syb_first")
     ap.add_argument("--comm-steps", type=int, default=2,
-                    help="N > 1: untimed diagnostic steps after the timed region whose "
+                    help="--full, N > 1: untimed diagnostic steps after the timed region whose "
                          "collectives are HIP-event timed (the line's 'comm' report)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # launcher-less form (`python bench.py --gpus N`): start the N ranks here, before
@@ -342,6 +393,10 @@ def main():
             print(f"bench.py: process group has {dist.get_world_size()} ranks, --gpus "
                   f"{args.gpus}", file=sys.stderr, flush=True)
             return 2
+
+    # the per-step dropout seeds come from torch's CPU generator: seed it, so that the same
+    # arguments give the same inputs and masks from run to run
+    torch.manual_seed(0)
 
     import savqa_amd  # noqa: F401
     from savqa_amd import ops
@@ -396,7 +451,7 @@ def main():
         opt.zero_grad()
         loss.backward()
         opt.step(reducer=reducer)
-        return loss
+        return loss, (lc, lv, ls, mil, mil_rel)
 
     for _ in range(args.warmup):
         step()
@@ -406,12 +461,15 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, outs = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, outs)
+    comm_steps = args.comm_steps if args.full else 0
     comm = None
     if world > 1:
         # per-rank diagnosis of the exchange (untimed steps): this rank's own step time from
@@ -419,9 +477,9 @@ def main():
         # collective the summed collective time, the part that outlasted the backward
         # (exposed), and the dense / row bytes
         mine = {"rank": rank, "ms_per_step": round(elapsed / args.steps * 1e3, 3)}
-        if args.comm_steps > 0:
+        if comm_steps > 0:
             reducer.time_collectives(True)
-            for _ in range(args.comm_steps):
+            for _ in range(comm_steps):
                 step()
             mine.update(reducer.comm_summary() or {})
             reducer.time_collectives(False)
@@ -431,7 +489,7 @@ def main():
         comm = {"bucket_mb": args.bucket_mb, "bwd_order": eng.bwd_order,
                 "bwd_schedule": (eng.AUTO_GATE if eng.multi_rank else "concurrent")
                 if eng.bwd_order == "auto" else eng.bwd_order,
-                "diag_steps": args.comm_steps, "ranks": ranks_c}
+                "diag_steps": comm_steps, "ranks": ranks_c}
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -449,7 +507,7 @@ def main():
     peak = BF16_MFMA_PEAK_TFLOPS if lp else FP32_MFMA_PEAK_TFLOPS
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # per-kernel timing needs kernels that do not share the GPU: run the probe steps
         # with both stacks on one stream (the timed region above overlaps them)
         probe = ops.GemmProbe()
@@ -494,7 +552,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
             cpu = cpu_baseline(args.cpu_seconds, rate=args.dropout)
         out = {
             "metric": METRIC, "value": round(value, 2), "unit": "QA-samples/s", "n_gpus": world,

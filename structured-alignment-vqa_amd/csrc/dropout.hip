@@ -53,40 +53,47 @@ __global__ __launch_bounds__(256) void posadd_dropout_kernel(
 
 // Backward: dz = Dx'(g) (written over g's buffer when dz == g), and
 //   dpos[t,c] += sum_b Dp'(dz[b,t,c])
-// One thread per (t, 4 columns, chunk of kBChunk samples), coalesced along c; the chunk
-// partial sums meet in dpos with atomics (B/kBChunk-way, fp32 order not fixed).
-constexpr int kBChunk = 32;
-__global__ __launch_bounds__(128) void posadd_dropout_bwd_kernel(
+// One block per (t, kPosQ groups of 4 columns): 256 threads = kPosQ column groups x kPosS
+// sample slices (slice s takes b = s, s + kPosS, ...), coalesced along c. The slices' partial
+// sums are folded through LDS in slice order by the slice-0 thread, which alone adds to its
+// dpos elements: the sum has a fixed order, so reruns are bit-identical (as period_sum_acc,
+// the no-dropout path).
+constexpr int kPosQ = 16, kPosS = 16;
+__global__ __launch_bounds__(kPosQ * kPosS) void posadd_dropout_bwd_kernel(
     const float* g, int64_t B, int64_t T, int64_t d, DropParam dp, int32_t site_pos,
-    uint32_t site_x, float* dz, float* __restrict__ dpos) {
+    uint32_t site_x, float* dz, float* dpos) {
   typedef float f4 __attribute__((ext_vector_type(4)));
-  const int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  __shared__ f4 part[kPosS][kPosQ];
+  const int q = threadIdx.x % kPosQ, sl = threadIdx.x / kPosQ;
+  const int64_t c = ((int64_t)blockIdx.x * kPosQ + q) * 4;
   const int64_t t = blockIdx.y;
-  if (c >= d) return;
   f4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int64_t b1 = min(B, (int64_t)(blockIdx.z + 1) * kBChunk);
-  for (int64_t b = (int64_t)blockIdx.z * kBChunk; b < b1; ++b) {
-    const int64_t i4 = (b * T + t) * d + c;
-    f4 v = *reinterpret_cast<const f4*>(g + i4);
-    v.x *= drop_mul(dp, site_x, i4);
-    v.y *= drop_mul(dp, site_x, i4 + 1);
-    v.z *= drop_mul(dp, site_x, i4 + 2);
-    v.w *= drop_mul(dp, site_x, i4 + 3);
-    *reinterpret_cast<f4*>(dz + i4) = v;
-    if (site_pos >= 0) {
-      v.x *= drop_mul(dp, site_pos, i4);
-      v.y *= drop_mul(dp, site_pos, i4 + 1);
-      v.z *= drop_mul(dp, site_pos, i4 + 2);
-      v.w *= drop_mul(dp, site_pos, i4 + 3);
+  if (c < d) {
+    for (int64_t b = sl; b < B; b += kPosS) {
+      const int64_t i4 = (b * T + t) * d + c;
+      f4 v = *reinterpret_cast<const f4*>(g + i4);
+      v.x *= drop_mul(dp, site_x, i4);
+      v.y *= drop_mul(dp, site_x, i4 + 1);
+      v.z *= drop_mul(dp, site_x, i4 + 2);
+      v.w *= drop_mul(dp, site_x, i4 + 3);
+      *reinterpret_cast<f4*>(dz + i4) = v;
+      if (site_pos >= 0) {
+        v.x *= drop_mul(dp, site_pos, i4);
+        v.y *= drop_mul(dp, site_pos, i4 + 1);
+        v.z *= drop_mul(dp, site_pos, i4 + 2);
+        v.w *= drop_mul(dp, site_pos, i4 + 3);
+      }
+      acc += v;
     }
-    acc += v;
   }
-  if (dpos) {
-    float* o = dpos + t * d + c;
-    atomicAdd(o, acc.x);
-    atomicAdd(o + 1, acc.y);
-    atomicAdd(o + 2, acc.z);
-    atomicAdd(o + 3, acc.w);
+  if (!dpos) return;  // uniform over the grid
+  part[sl][q] = acc;
+  __syncthreads();
+  if (sl == 0 && c < d) {
+    f4 sum = part[0][q];
+    for (int k = 1; k < kPosS; ++k) sum += part[k][q];
+    f4* o = reinterpret_cast<f4*>(dpos + t * d + c);
+    *o = *o + sum;
   }
 }
 
@@ -129,8 +136,8 @@ extern "C" int savqa_posadd_dropout_bwd(void* stream, const float* g, int64_t B,
     return fail(SAVQA_EINVAL, "savqa_posadd_dropout_bwd: d must be a multiple of 4, p in [0,1]");
   if (((uintptr_t)g | (uintptr_t)dz | (uintptr_t)dpos) & 15)
     return fail(SAVQA_EINVAL, "savqa_posadd_dropout_bwd: buffers must be 16-byte aligned");
-  hipLaunchKernelGGL(posadd_dropout_bwd_kernel, dim3((d / 4 + 127) / 128, T, (B + kBChunk - 1) / kBChunk), dim3(128), 0,
-                     as_stream(stream), g, B, T, d, make_drop(seed, p), site_pos, (uint32_t)site_x,
-                     dz, dpos);
+  hipLaunchKernelGGL(posadd_dropout_bwd_kernel, dim3((d / 4 + kPosQ - 1) / kPosQ, T),
+                     dim3(kPosQ * kPosS), 0, as_stream(stream), g, B, T, d, make_drop(seed, p),
+                     site_pos, (uint32_t)site_x, dz, dpos);
   return check_launch("savqa_posadd_dropout_bwd");
 }

@@ -33,7 +33,7 @@ def test_bench_two_ranks_gloo_rehearsal(workload):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
            "--workload", workload, "--batch", "32", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-roofline"]
+           "--full", "--no-cpu-baseline", "--no-roofline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -62,7 +62,7 @@ def test_bench_comm_flags_two_ranks():
     env = dict(os.environ, SAVQA_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
-           "--batch", "16", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+           "--batch", "16", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-roofline", "--bucket-mb", "256", "--bwd-gate", "concurrent", "--comm-steps", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -77,6 +77,43 @@ def test_training_step_gradients_bit_identical(prec):
     assert int((tab.abs().sum(1) > 0).sum()) <= 40 and float(tab.abs().max()) > 0
 
 
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_training_step_with_dropout_bit_identical(prec):
+    """The same step under training dropout (0.5, the reference default), its seed drawn from
+    torch's generator re-seeded before each run: the masks repeat, the position tables'
+    gradient (savqa_posadd_dropout_bwd) is summed in a fixed order, and every output and
+    gradient is bit-identical again."""
+    from savqa_amd import ops
+    from savqa_amd.data import model_args
+    from savqa_amd.loss import smoothed_loss
+    if not ops.DET_SCATTER:
+        pytest.skip("SAVQA_DET_SCATTER=0: the atomic table scatters are run-order dependent")
+    m = _model(prec, dropout=0.5)
+    b = _dup_batch(64)
+    a = m._arena
+    runs = []
+    for _ in range(3):
+        torch.manual_seed(17)
+        lc, lv, ls, mil, _ = m(*model_args(b), decMask=True, mcb=False)
+        loss, _ = smoothed_loss(lc, lv, ls, b["answer"], mil)
+        m.zero_grad(set_to_none=False)
+        loss.backward()
+        torch.cuda.synchronize()
+        runs.append((torch.cat([lc, lv, ls]).detach().clone(), a.grad[:a.n_live].clone()))
+    assert m._last_dropout is not None and m._last_dropout[1] == 0.5
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][0], runs[2][0])
+    bad = []
+    for n in a.live_names:
+        o, shp = a.offsets[n]
+        x = [g[o:o + shp.numel()] for _, g in runs]
+        if not (torch.equal(x[0], x[1]) and torch.equal(x[0], x[2])):
+            bad.append(n)
+    assert not bad, bad
+    for pre in ("att_vis_grid", "att_syb"):  # the position tables did get a gradient
+        pos = [n for n in a.live_names if n.startswith(pre) and "position" in n]
+        assert pos and all(float(a.view(n, runs[0][1]).abs().max()) > 0 for n in pos), pos
+
+
 def test_segment_add_rows_matches_index_add():
     """savqa_segment_add_rows against fp64 index_add over ragged runs (ids with 1..50
     duplicates, ids absent, a strided source), and bit-identical reruns."""

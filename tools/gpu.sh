@@ -39,7 +39,7 @@ case "$cmd" in
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 \
       || { tail -20 gpurun_out/smoke.log; exit 1; }
     tail -2 gpurun_out/smoke.log
-    bench_line cfg2
+    bench_line cfg2 --full
     ;;
   tests)
     timeout -k 10 ${TO} python -u -m pytest -x -v --timeout 280 --timeout-method thread "$@" \
@@ -49,7 +49,7 @@ case "$cmd" in
     ;;
   bench)
     for w in ${@:-cfg2}; do
-      if [ "$w" = cfg2 ]; then bench_line cfg2; else bench_line "$w" --no-cpu-baseline; fi
+      bench_line "$w" --full
     done
     ;;
   prof)

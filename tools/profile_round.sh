@@ -14,7 +14,7 @@ STEPS=${STEPS:-5}
 O=gpurun_out/prof_${TAG}_${WL}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-CMD="python bench.py --workload $WL --steps $STEPS --warmup 2 --no-cpu-baseline"
+CMD="python bench.py --workload $WL --steps $STEPS --warmup 2 --full --no-cpu-baseline"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- $CMD > $O/bench_trace.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- $CMD > $O/bench_fetch.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- $CMD > $O/bench_write.log 2>&1

@@ -3,9 +3,9 @@
 
 usage: summarize_prof.py TRACE_DIR PMC_FETCH_DIR PMC_WRITE_DIR OUT_PREFIX LAUNCHES_PER_STEP_JSON
 
-* TRACE_DIR: `rocprofv3 --kernel-trace --stats` of `python bench.py ...` (the judged command).
+* TRACE_DIR: `rocprofv3 --kernel-trace --stats` of `python bench.py --full ...`.
   Copies its kernel stats and adds the per-kernel average over the LAST 2 steps' launches of
-  each GEMM variant (bench.py's roofline probe runs 2 serial steps at the end).
+  each GEMM variant (bench.py --full's roofline probe runs 2 serial steps at the end).
 * PMC_*_DIR: separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of the same command.
   HBM bytes per launch = 2 x FETCH_SIZE (gfx950 reports half the bytes of wide coalesced
   reads, MI355X_MICROARCH.md HBM section) + WRITE_SIZE, both in KB -> bytes.
